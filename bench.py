@@ -22,11 +22,18 @@ renders its blocks and rank 0 gathers the framebuffer slices with ONE RCCL gathe
     "nccl" (RCCL) process group and runs the frame's gather collective with world size 1 -- the multi-GPU code path on
     the one GPU a box has (`rccl_ranks: 1` in the line).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, renders the scene's first frame, warms up, times the K steps and
+prints the headline (`value`, `ms_per_step` = wall time of one timed step) with the per-rank kernel, setup and first-frame
+times it saw on the way.  `--full` adds everything that needs work of its own:
+  value_e2e     extra steps with the D2H copy of the float frame inside the clock
+  parity_check  pixels of the last frame against the CPU oracle
   roofline      algorithmic flops per launch (SURVEY 8d formula, counters from the CPU oracle's instrumented walk
                 of the same BVH) / mean kernel duration from HIP events on the launch stream; `traffic`: HBM-side bytes per
                 step from FETCH_SIZE / WRITE_SIZE, measured in this run by two rocprofv3 child runs of this command (N = 1)
+  linear_scan_kernel  the reference's linear scan on the same frame, on the GPU
   cpu_baseline  the oracle (a port of the reference's CPU path, reference-shaped job system) timed on this host
+`--dump-outputs DIR` writes the frame of the last timed step (see dump_outputs()); scene and render seeds are fixed, so the
+same arguments give the same inputs in every run.
 """
 import os
 
@@ -114,6 +121,11 @@ def parse_args(argv=None):
                     help="one process, N devices, through rtmi_frame_* (RCCL inside librtmi.so)")
     ap.add_argument("--force-dist", action="store_true",
                     help="world size 1 through the multi-GPU path: launcher, RCCL process group and the gather collective")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure value_e2e, the oracle parity check, the roofline (with its rocprofv3 child runs), the "
+                         "linear-scan kernel and the CPU baseline; a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-linear-scan", action="store_true", help="skip the extra linear-scan (reference algorithm) step")
     ap.add_argument("--no-e2e", action="store_true", help="skip the extra D2H-inclusive steps behind value_e2e")
@@ -233,6 +245,31 @@ def workload(pkg, cfg, args):
     return kw, objs, mats, label
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: at most this many bytes of arrays (a 1080p frame is 58 MB)
+
+
+def dump_outputs(out_dir, rgb, rgba8, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the two arrays a caller of the timed path receives, as float32 .npy files in out_dir --
+    rgb.npy (H, W, 3) linear RGB, bit for bit, and rgba8.npy (H, W, 4) the packed 0xAABBGGRR words as R, G, B, A bytes
+    (0..255).  A frame larger than `budget` is cut to a fixed seeded sample of pixels, the same one for the same frame
+    size: rgb.npy (n, 3), rgba8.npy (n, 4) and pixel_index.npy (n,) = y * W + x in float64.  Returns the names written."""
+    import numpy as np
+    H, W = rgb.shape[:2]
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(H * W, 3)
+    rgba = np.ascontiguousarray(rgba8).view(np.uint32).reshape(H * W).view(np.uint8).reshape(H * W, 4).astype(np.float32)
+    per_pixel = rgb.itemsize * 3 + rgba.itemsize * 4
+    if H * W * per_pixel <= budget:
+        arrays = {"rgb": rgb.reshape(H, W, 3), "rgba8": rgba.reshape(H, W, 4)}
+    else:
+        n = budget // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(RENDER_SEED).choice(H * W, n, replace=False))
+        arrays = {"rgb": rgb[idx], "rgba8": rgba[idx], "pixel_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def rehearse(args, world, rank):
     """Launcher + gather plumbing on CPU tensors (gloo): every rank fills its slice with the absolute row number, rank 0
     gathers and checks scanline order.  No render, no GPU; the line says so."""
@@ -275,6 +312,8 @@ def main(argv=None):
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if (args.gpus > 1 or args.force_dist) and world_env is None and not args.single_process:
         sys.exit(launch_ranks(args, argv))  # this process never touches the GPU
 
@@ -290,7 +329,7 @@ def main(argv=None):
         return rehearse(args, world, rank)
 
     live_traffic = (None, "not measured (--no-traffic, a multi-GPU run or --single-process): the figure of profiles/hbm_traffic.json")
-    if world == 1 and not args.single_process and not args.no_traffic and not args.force_dist:
+    if args.full and world == 1 and not args.single_process and not args.no_traffic and not args.force_dist:
         live_traffic = measure_traffic(args)  # child processes; this one has not touched the GPU yet
 
     import numpy as np
@@ -451,6 +490,13 @@ def main(argv=None):
     if gather_events:  # (all steps are done: the events have completed)
         gather_ms.extend(a.elapsed_time(b) for a, b in gather_events)
         gather_events.clear()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if args.single_process:  # (the frame stays on the first device: rtmi_frame_render renders the same seed again to host)
+            dump_rgb, dump_rgba = frame_obj.render(RENDER_SEED)
+        else:
+            dump_rgb, dump_rgba = frame.cpu().numpy(), frame8.cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, dump_rgb, dump_rgba)
     # what every rank saw, for a line that explains itself when N > 1: its own first frame (allocations, the cost
     # probe), its mean trace-kernel span, its mean gather + de-interleave time (rank 0: until the frame is in scanline order;
     # the others: until their slice has left)
@@ -478,9 +524,9 @@ def main(argv=None):
         print(json.dumps({"traffic_child": True, "steps": args.steps, "kernel_ms": per_rank_ms}), flush=True)
         scene.close()
         return
-    # ---- the metric as SURVEY 8(d) words it: wall time including the D2H copy of the float frame (+ gather) ------------
+    # ---- --full: the metric as SURVEY 8(d) words it: wall time including the D2H copy of the float frame (+ gather) -----
     e2e_elapsed, e2e_steps = None, 0
-    if not args.no_e2e and not args.single_process:
+    if args.full and not args.no_e2e and not args.single_process:
         e2e_steps = max(1, min(args.steps, 3))
         host = torch.empty((H, W, 3), dtype=torch.float32, pin_memory=True) if rank == 0 else None
         sync()
@@ -495,7 +541,7 @@ def main(argv=None):
         if use_dist:
             dist.all_reduce(te, op=dist.ReduceOp.MAX)
         e2e_elapsed = float(te.item())
-    elif args.single_process and not args.no_e2e:
+    elif args.full and args.single_process and not args.no_e2e:
         e2e_steps = max(1, min(args.steps, 3))
         t1 = time.perf_counter()
         for _ in range(e2e_steps):
@@ -532,7 +578,7 @@ def main(argv=None):
             # SURVEY 8(d)'s wording of the metric (D2H of the frame inside the clock) is `value_e2e` below
             "value_resident": round(value, 2),
             "value_definition": "W*H*spp / wall time of the K timed steps, scene + BVH resident, frame left in HBM (gather included "
-                                "for N > 1); value_e2e = the same with the D2H copy of the float frame inside the clock",
+                                "for N > 1); value_e2e (--full) = the same with the D2H copy of the float frame inside the clock",
             "scene_setup_ms": round(scene_setup_ms, 2),
             "scene_setup_note": "rtmi_scene_create on rank 0: SAH BVH build on the host + upload of spheres, materials and nodes",
             "first_frame_ms": round(first_frame_ms, 2),
@@ -549,6 +595,11 @@ def main(argv=None):
             out["value_e2e"] = round(samples / (e2e_elapsed / e2e_steps) / 1e6, 2)
             out["value_e2e_note"] = (f"{e2e_steps} extra steps timed with the D2H copy of the {W}x{H} float frame into pinned "
                                      "host memory (and the gather) inside the clock: the metric as SURVEY 8(d) words it")
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": [n + ".npy" for n in dumped],
+                                     "note": "the frame of the last timed step, float32 (dump_outputs() in bench.py)"}
+    # ---- --full: everything below needs work of its own (the oracle on the CPU, extra GPU launches) --------------------------
+    if rank == 0 and args.full:
         if args.single_process:
             frame = torch.from_numpy(host_rgb) if e2e_elapsed is not None else None
         # ---- parity spot check + algorithmic work counters from the CPU oracle (checker only) -------------
@@ -716,6 +767,7 @@ def main(argv=None):
             out["gpu_over_cpu_note"] = "GPU: BVH walk (same frame as the scan, bit for bit); CPU: the reference's linear scan"
             if lin_rate is not None:
                 out["gpu_over_cpu_like_for_like"] = round(lin_rate / (n / secs / 1e6), 1)
+    if rank == 0:
         print(json.dumps(out), flush=True)
 
     if scene is not None:

@@ -725,7 +725,7 @@ def test_bench_force_dist_runs_the_rccl_process_group_with_one_rank(gpu):
     import sys
     from tests.conftest import ROOT
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--config", "2", "--width", "160",
-            "--spp", "8", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--no-linear-scan"]
+            "--spp", "8", "--steps", "2", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-linear-scan"]
     for extra in ([], ["--single-process"]):
         r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -733,6 +733,39 @@ def test_bench_force_dist_runs_the_rccl_process_group_with_one_rank(gpu):
         assert doc["rccl_ranks"] == 1 and doc["n_gpus"] == 1 and doc["value"] > 0, doc
         if not extra:
             assert doc["parity_check"]["max_abs_diff_vs_oracle"] == 0.0 and "nccl" in doc["config"]["launcher"]
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_frame(pkg, gpu, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline and nothing that needs work of its own; `--dump-outputs DIR`
+    writes the frame of the last timed step, which is the frame rtmi_render_rows gives for the same scene and seed -- through
+    the torch path and through rtmi_frame_* (`--single-process`)."""
+    import subprocess
+    import sys
+    from tests.conftest import ROOT
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "2", "--width", "160", "--spp", "8",
+            "--steps", "3", "--warmup", "1"]
+    kw = dict(image_width=160, samples_per_pixel=8, max_depth=50)
+    cam = pkg.camera_setup(pkg.camera_params(**kw))
+    with pkg.Scene(cam, *pkg.make_world_spheres(12345), accel=pkg.ACCEL_BVH) as s:
+        want, want8 = s.render_rows(0, cam.img_height, 2025)  # (bench.py's SCENE_SEED and RENDER_SEED)
+    for extra in ([], ["--single-process"]):
+        out = tmp_path / ("dump" + "".join(extra))
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        doc = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in doc, k
+        assert doc["steps"] == 3 and doc["warmup"] == 1 and doc["ms_per_step"] > 0 and doc["value"] > 0
+        for k in ("value_e2e", "parity_check", "roofline", "linear_scan_kernel", "cpu_baseline"):
+            assert k not in doc, k
+        assert doc["dumped_outputs"]["files"] == ["rgb.npy", "rgba8.npy"]
+        rgb, rgba8 = np.load(out / "rgb.npy"), np.load(out / "rgba8.npy")
+        assert rgb.dtype == np.float32 and rgba8.dtype == np.float32
+        assert rgb.shape == want.shape and rgba8.shape == want.shape[:2] + (4,)
+        assert rgb.tobytes() == want.tobytes()
+        assert np.array_equal(rgba8.astype(np.uint8), want8.view(np.uint8).reshape(rgba8.shape))
 
 
 def test_multi_device_frame_over_rccl(pkg, rtow, gpu):

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/prof_${TAG}_config${CFG}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "== bench config $CFG"
-python3 $ROOT/bench.py --config $CFG "$@" > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+python3 $ROOT/bench.py --config $CFG --full "$@" > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 cut -c1-400 $OUT/bench.json
 QUIET="--config $CFG --no-cpu-baseline --no-linear-scan --no-e2e --no-traffic --steps $STEPS --warmup 0"
 echo $((STEPS + 1)) > $OUT/frames.txt   # frames of a traced run: the first frame of the scene + the steps
